@@ -24,9 +24,15 @@ segment, as one graph / as 25 chunk steps of 5 M samples in one cached graph).
 
 Output: one JSON line on rank 0 (contract in the task statement) with `roofline` for the
 dominant kernel (HIP events on its stream; `traffic` from the committed rocprofv3 PMC summary
-profiles/pmc_traffic.json), `arithmetic` naming the kernel's number format, and `cpu_baseline`
-(the oracle's float32 direct form on the host's cores, rank 0, N = 1, with the C1 config as a
-second CPU line).
+profiles/pmc_traffic.json) and `arithmetic` naming the kernel's number format.
+
+A plain run sets up, warms up, times the K steps and prints that line. `--full` adds everything
+that takes runs of its own: `cpu_baseline` (the oracle's float32 direct form on the host's cores,
+rank 0, N = 1, with the C1 config as a second CPU line), the in-process HBM bandwidth probe
+(`roofline.measured_*`) and, for c3, the secondary workloads under `extras`.
+
+`--dump-outputs DIR` writes what the last timed step computed (the step's output array as its
+caller receives it) to DIR/<name>.npy as float32; see dump_outputs.
 """
 from __future__ import annotations
 
@@ -215,6 +221,10 @@ class ShardedChain:
                 nxt.ring.halo.copy_(sl.ring.tail)
         self.cur = (self.cur + 1) % self.n_slots
 
+    def last_outputs(self):
+        """{name: tensor} the most recent step handed to its caller: the AM envelope of its segment."""
+        return {"am": self.slots[(self.cur - 1) % self.n_slots].out}
+
     @property
     def kernel_class(self):
         x = self.slot.buf if self.single else self.slot.bulk_x
@@ -280,6 +290,10 @@ class AmChainSharded:
         if self.n_slots > 1 and g.world > 1 and g.rank == 0:
             nxt.ring.halo.copy_(sh.ring.halo)
         self.cur = (self.cur + 1) % self.n_slots
+
+    def last_outputs(self):
+        """{name: tensor} the most recent step handed to its caller: the audio of its segment."""
+        return {"audio": self.slots[(self.cur - 1) % self.n_slots].out}
 
     def timed_bytes_ops(self):
         """Per step (the timed region is the whole step: RF FIR + AM bulk and head, audio FIR):
@@ -363,11 +377,15 @@ class AmChainRunner:
             if ev is not None:
                 ev[0].record(self.stream)
             if self.mode == "resident":
-                self.chain.step_resident(self.iq, self.chunks, self.out)
+                self.n_audio = self.chain.step_resident(self.iq, self.chunks, self.out)
             else:  # live-stream chunks, all of a step's chunk steps as one cached graph launch
-                self.chain.step_chunks(self.iq, self.chunks, self.out)
+                self.n_audio = self.chain.step_chunks(self.iq, self.chunks, self.out)
             if ev is not None:
                 ev[1].record(self.stream)
+
+    def last_outputs(self):
+        """{name: tensor} the most recent step handed to its caller: the audio samples it returned."""
+        return {"audio": self.out[: self.n_audio]}
 
     def timed_bytes_ops(self):
         """Per timed region (all chunks of a step): int8 input read once + audio written once; the
@@ -602,6 +620,11 @@ def timed_steps(chain, steps, warmup, world, backend, device, local, ops):
             # long at the barrier before the timed steps would start them after an idle gap
             dist.barrier()
         settle(chain.step, world=world, device=device, backend=backend)
+        # the settle runs for a time, not a count: go on (untimed) to the wrap of the slot ring, so that
+        # the timed steps read the same slots, with the same history in front of them, in every run
+        # (every rank holds the same slot index, so every rank adds the same number of steps)
+        while getattr(chain, "cur", 0) != 0:
+            chain.step()
         for _ in range(warmup):
             chain.step()
         ops.fft_direct_blocks(local, reset=True)
@@ -938,13 +961,38 @@ def host_step_costs(ops, device, steps=60):
     return host
 
 
+DUMP_MAX_ELEMS = 1 << 22  # float32 elements written per output array (16 MiB)
+
+
+def dump_outputs(chain, out_dir, rank, world):
+    """--dump-outputs: the arrays the last step handed to its caller, as <out_dir>/<name>.npy (float32;
+    `<name>_rank<r>` with several ranks). An array of more than DUMP_MAX_ELEMS / world elements is
+    written as a fixed sample: the elements at that many sorted indices drawn without replacement by
+    a generator seeded with the array's length, so two builds write the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    for name, t in chain.last_outputs().items():
+        a = t.detach().cpu().numpy().astype(np.float32, copy=False)
+        keep = DUMP_MAX_ELEMS // world  # the ranks' files together stay at 16 MiB per output
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the in-process HBM "
+                         "bandwidth probe and (c3) the secondary workloads under 'extras'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's output arrays to DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of an array above 2^22 elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--c5-mode", default="sharded", choices=["sharded", "resident", "chunked"],
                     help="c5: the time-sharded chain with its cascaded halo (default); or the gsdrAmChain "
                          "executor: one graph over the resident 1 s segment / one graph per 5 M-sample chunk "
@@ -955,8 +1003,8 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="run every rank on cuda:0 (testing the multi-rank path on a one-GPU box; gloo)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements (C4 strong scaling, C5, C2, the C3 node path and stream) that the "
-                         "default run adds to its JSON line under 'extras'")
+                    help="with --full: skip the secondary measurements (C4 strong scaling, C5, C2, the C3 node path and "
+                         "stream) that a --full run adds to its JSON line under 'extras', and the HBM probe")
     ap.add_argument("--kernel-policy", type=int, default=0,
                     help="gsdrAmdSetKernelPolicy flags for A/B runs (e.g. 64 = GSDR_POLICY_I8_WS8, the r04 8-way int8 "
                          "kernel); recorded in the line's config when nonzero")
@@ -988,13 +1036,16 @@ def main():
     achieved_t = ops_ / (kernel_ms * 1e-3) / 1e12
     total_samples = world * chain.L * args.steps
     value = total_samples / elapsed / 1e6
+    if args.dump_outputs:
+        dump_outputs(chain, args.dump_outputs, rank, world)
+    extras_on = args.full and not args.no_extras
 
     # secondary workloads in the same run, so the driver's 1/2/4/8-GPU runs measure every config
     # BASELINE.json names: C4 as stated (one 2^30-sample stream split over the GPUs, strong scaling),
     # the C5 chain, C2 (configs[1], the HackRF-shaped int8 chain), and (N = 1) C3 through the
     # reference's node API
     extras = {}
-    if args.workload == "c3" and not args.no_extras:
+    if args.workload == "c3" and extras_on:
         if world == 1:
             extras["c3_mixed"] = mixed_vs_plain(ops, chain)
         chain_info = (chain.kernel_class, kernel_name(chain), chain.L, chain.T, chain.D, chain.kind, chain.geom,
@@ -1018,12 +1069,12 @@ def main():
     else:
         kernel_label = kernel_name(chain)
     # measured bandwidth in this process, the second reference of the roofline
-    probe = hbm_probe(ops, device) if not args.no_extras else None
+    probe = hbm_probe(ops, device) if extras_on else None
 
     if rank == 0:
         desc = WORKLOADS[args.workload][0]
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.workload)
         traffic, traffic_src = load_traffic(args.workload)
         rf_traffic = None

@@ -42,9 +42,9 @@ for s in "$@"; do
             step c5_ws4_$r 300 python -u bench.py --workload c5 --no-extras --no-cpu-baseline --steps 60 --warmup 5
             step c5_ws8_$r 300 python -u bench.py --workload c5 --no-extras --no-cpu-baseline --steps 60 --warmup 5 --kernel-policy 64
           done ;;
-    bench) step bench_default 600 python -u bench.py ;;
+    bench) step bench_default 600 python -u bench.py --full ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-            python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
+            python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ;;
     hostfed) step hostfed 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$OUT/hostfed" -o run -- \
                python3 tools/exp/host_fed_probe.py ;;
     hostapi) step hostapi 300 rocprofv3 --hip-runtime-trace --kernel-trace --memory-copy-trace --output-format csv \
@@ -52,7 +52,7 @@ for s in "$@"; do
     waits) GSDR_LIB=$PWD/tools/exp/_ablib/waits/libgpusdrpipeline.so step c5_waits_ws4 300 python3 -u tools/exp/c5_waits_probe.py
            GSDR_LIB=$PWD/tools/exp/_ablib/waits/libgpusdrpipeline.so step c5_waits_ws8 300 python3 -u tools/exp/c5_waits_probe.py --ws8 ;;
     t:*) step "test_${s#t:}" 600 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread -k "${s#t:}" ;;
-    ranks8) step ranks8 900 python -u bench.py --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 ;;
+    ranks8) step ranks8 900 python -u bench.py --full --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done

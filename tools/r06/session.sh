@@ -33,12 +33,12 @@ for s in "$@"; do
   case "$s" in
     tests) step tests 900 $PYT tests ;;
     smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench_default 600 python -u bench.py ;;
+    bench) step bench_default 600 python -u bench.py --full ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-            python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline ;;
+            python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ;;
     c5n2) step c5_n2 420 python -u bench.py --workload c5 --gpus 2 --share-gpu --backend gloo --no-extras \
             --no-cpu-baseline --steps 20 --warmup 3 ;;
-    ranks8) step ranks8 900 python -u bench.py --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 ;;
+    ranks8) step ranks8 900 python -u bench.py --full --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 ;;
     t:*) step "test_${s#t:}" 600 $PYT tests -k "${s#t:}" ;;
     f:*) step "file_${s#f:}" 600 $PYT "tests/${s#f:}.py" -v ;;
     py:*) step "py_$(basename "${s#py:}" .py)" 600 python3 -u "${s#py:}" ;;
