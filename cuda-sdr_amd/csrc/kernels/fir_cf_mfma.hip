@@ -157,6 +157,18 @@ __device__ __forceinline__ void directTile(const CfFirArgs& a, int tile, int tid
   else reinterpret_cast<f2*>(a.out)[k] = f2{(float)yr, (float)yi};
 }
 
+// amEnvelope of an unscaled fp32 sum: below |z| ~ 2^-63 the larger square is an fp32 subnormal and the
+// envelope loses its bits (a window whose samples meet only a Blackman filter's tail taps: 1e-20 of the
+// largest). The switch sits well above that limit, at 2^-40 - where is free, both sides being the same
+// expression: outputs below it are squared as z 2^100 (squares < 2^120: no overflow; the smallest subnormal
+// input squares to 2^-98: normal); from 2^-40 up, every output the parity tests and the benchmark see, it is
+// amEnvelope itself, bit for bit. (The f16 kernels square sums scaled to the tile, the direct tiles in double.)
+__device__ __forceinline__ float amEnvelopeUnscaled(f2 z) {
+  const float m = fmaxf(fabsf(z.x), fabsf(z.y));
+  if (!(m < 0x1p-40f) || m == 0.0f) return amEnvelope(z);  // NaN included
+  return amEnvelope(z * 0x1p100f) * 0x1p-100f;
+}
+
 template <int KS, int G, int EPI>
 __global__ __launch_bounds__(kCfThreads, 1) void firCfMfmaKernel(CfFirArgs a) {
   extern __shared__ __attribute__((aligned(16))) int8_t smem[];
@@ -262,7 +274,7 @@ __global__ __launch_bounds__(kCfThreads, 1) void firCfMfmaKernel(CfFirArgs a) {
     const int orow = (wave & 3) + 8 * (wave >> 2) + 4 * half;
     const int64_t k = (int64_t)tile * kCfTileOut + 32 * orow + col;
     if (k < a.nOut) {
-      if (EPI == kEpiAm) reinterpret_cast<float*>(a.out)[k] = amEnvelope(f2{yi, yq});
+      if (EPI == kEpiAm) reinterpret_cast<float*>(a.out)[k] = amEnvelopeUnscaled(f2{yi, yq});
       else reinterpret_cast<f2*>(a.out)[k] = f2{yi, yq};
     }
     }
@@ -1115,15 +1127,27 @@ __device__ __forceinline__ void loadWindowI8(const I8DecArgs& a, int tile, int t
   }
 }
 
+// The zero-window guard's flags on the way (ws_common.h): zf[wave] gets bit 0 when this wave's units hold two
+// adjacent all-zero ones inside the tile's window and the input (wsI8ZeroPair), bit 1 when one of its units
+// there is not zero. A tile with both is computed in the direct form; an all-zero window's MFMA result is
+// exactly 0 already.
 template <int G>
-__device__ __forceinline__ void splitWindowI8(const I8DecArgs& a, const I8DecWindow<G>& w, int8_t* planes, int tid) {
+__device__ __forceinline__ void splitWindowI8(const I8DecArgs& a, const I8DecWindow<G>& w, int8_t* planes, int tid,
+                                              int tile, int* zf) {
+  const int lane = tid & (kWave - 1);
+  const uint32_t edge = 0u - (uint32_t)(((lane + 1) >> 6) | ((64 - lane) >> 6));  // lanes 0, 63
+  const int Wl = min(a.Wu, (511 * a.D + a.T + 7) >> 3);
+  const int Wz = wsClampI64((a.nIn - (int64_t)tile * kCfTileOut * a.D) >> 3, Wl);
+  uint32_t zmin = 0xffffffffu, any = 0u;
 #pragma unroll
   for (int j = 0; j < G; ++j) {
     const int g = tid + kCfThreads * j;
-    if (g < a.Wu) {
-      uint32_t words[4];
+    uint32_t words[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) words[q] = __builtin_amdgcn_alignbyte(w.d[j][q + 1], w.d[j][q], a.sub);
+    for (int q = 0; q < 4; ++q) words[q] = __builtin_amdgcn_alignbyte(w.d[j][q + 1], w.d[j][q], a.sub);
+    zmin = min(zmin, wsI8ZeroPair(words, g, Wz, edge));
+    any |= g < Wz ? words[0] | words[1] | words[2] | words[3] : 0u;
+    if (g < a.Wu) {
       uint4 iu, qu;
       int8IqToF16Units(words, iu, qu);
       const int off = 16 * cfPhys(g, a.padShift);
@@ -1131,6 +1155,8 @@ __device__ __forceinline__ void splitWindowI8(const I8DecArgs& a, const I8DecWin
       *reinterpret_cast<uint4*>(planes + a.planeStride + off) = qu;
     }
   }
+  const int f = (__ballot(zmin == 0u) != 0ull ? 1 : 0) | (__ballot(any != 0u) != 0ull ? 2 : 0);
+  if (lane == 0) zf[tid >> 6] = f;
 }
 
 template <int KS, int G, int EPI>
@@ -1139,6 +1165,9 @@ __global__ __launch_bounds__(kCfThreads, 1) void firI8DecMfmaKernel(I8DecArgs a)
   int8_t* planes = smem;
   float* part = reinterpret_cast<float*>(smem + 2 * a.planeStride);
   __shared__ float waveMax[kCfWaves];
+  // zero-window guard: the waves' flags of a tile, by tile parity (tile i + 1 is split while slower waves
+  // still read tile i's in their epilogue)
+  __shared__ int zf[2][kCfWaves];
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -1193,7 +1222,7 @@ __global__ __launch_bounds__(kCfThreads, 1) void firI8DecMfmaKernel(I8DecArgs a)
   }
   __syncthreads();  // the tap staging area becomes the partial-sum area
 
-  splitWindowI8<G>(a, win, planes, tid);
+  splitWindowI8<G>(a, win, planes, tid, t0, zf[0]);
   if (n > 1) loadWindowI8<G>(a, t0 + 1, tid, win);
   __syncthreads();
 
@@ -1226,6 +1255,11 @@ __global__ __launch_bounds__(kCfThreads, 1) void firI8DecMfmaKernel(I8DecArgs a)
     }
     const int orow = (wave & 3) + 8 * (wave >> 2) + 4 * half;
     const int64_t k = (int64_t)tile * kCfTileOut + 32 * orow + col;
+    // the zero-window guard's tiles (a zero run beside signal) in the direct form, as the 8-way consumers
+    int zt = 0;
+#pragma unroll
+    for (int v = 0; v < kCfWaves; ++v) zt |= zf[i & 1][v];
+    if (waveUniform(zt) == 3 && k < a.nOut) wsI8DirectOutput(a.iq4 + a.sub, a.taps, T, D, k, sc, yi, yq);
     if (k < a.nOut) {
       if (EPI == kEpiAm) {
         reinterpret_cast<float*>(a.out)[k] = __builtin_amdgcn_sqrtf(fmaf(yi, yi, yq * yq)) * outScale;
@@ -1235,7 +1269,7 @@ __global__ __launch_bounds__(kCfThreads, 1) void firI8DecMfmaKernel(I8DecArgs a)
     }
 
     if (i + 1 < n) {
-      splitWindowI8<G>(a, win, planes, tid);
+      splitWindowI8<G>(a, win, planes, tid, tile + 1, zf[(i + 1) & 1]);
       if (i + 2 < n) loadWindowI8<G>(a, tile + 2, tid, win);
       __syncthreads();
     }

@@ -72,6 +72,17 @@ constexpr int kStoresPerChunk = kI8TilesPerWave * 8;
 constexpr int kLimbPad = 32;
 constexpr int kLimbRow = 256;
 static_assert(kLimbPad + 32 * kI8MaxS + 16 <= kLimbRow && 2 * kLimbRow * 2 == 4 * kI8Threads, "limb table");
+// The zero-window guard (ws_common.h has the decimating kernels'): the split pass notes, per 512 window
+// samples (stretch c), whether an 8-sample unit is exactly zero - zf[c] - and whether one of the stretch's
+// first 4 S - 4 units is - zf[kZfStretches + c]: the part of it the previous tile's window reaches (its last
+// sample is 512 (t + 1) + T - 2 <= 512 (t + 1) + 32 S - 33). A tile with such a unit inside its own window
+// (zf[t] | zf[kZfStretches + t + 1]) - any zero run of >= 15 samples: a zero-padded start, an exact-zero gap
+// - is computed in the direct form (tileDirect) by the wave that owns it, unless its window is zero throughout
+// (tileWindowZero): the MFMA result is exactly 0 then. A flagged tile costs 8 T serial double FMAs per lane
+// against 4 S MFMAs: a stream that is mostly but not wholly zero runs at the direct form's rate.
+constexpr int kZfStretches = 16;            // >= stretches per chunk window (9), the rest past the window
+constexpr int kZfWords = 2 * kZfStretches;  // whole-stretch flags, then head flags
+constexpr int kTapWords = 32 * kI8MaxS;  // the fp32 taps for the direct form, zero past T
 
 struct I8FirArgs {
   const int8_t* iq;   // interleaved I, Q (2-byte aligned)
@@ -171,11 +182,18 @@ __device__ __forceinline__ void issueChunk(uintptr_t alignedBase, uintptr_t last
 
 // Split one landed slot into the f16 I / Q planes: group g = samples [8g, 8g + 8) of the window
 // at window bytes [16 g, 16 g + 16); `win` is 4-byte aligned when sub = 0, else 2-byte aligned.
+// The zero-window guard's flags on the way (the four words of a group are in registers here): wave w's
+// pass u covers the 64 groups of window samples [512 c, 512 c + 512), c = 4 u + w, and sets zf[c] (zeroed
+// by the caller) when one of them is all zero, I = Q = 0 in 8 adjacent samples, and zf[kZfStretches + c]
+// when that group is one of the first 4 S - 4 - stores under the rare lanes' exec mask, nothing for the
+// scalar unit to wait for on dense input.
 template <int S>
-__device__ __forceinline__ void splitSlot(const int8_t* win, int8_t* planes, int sub, int tid) {
+__device__ __forceinline__ void splitSlot(const int8_t* win, int8_t* planes, int* zf, int sub, int tid) {
   using G = I8Geom<S>;
+  constexpr int kPasses = (G::kGroups + kI8Threads - 1) / kI8Threads;
+  static_assert(kI8Waves * kPasses <= kZfStretches, "zero-unit flags");
 #pragma unroll
-  for (int u = 0; u < (G::kGroups + kI8Threads - 1) / kI8Threads; ++u) {
+  for (int u = 0; u < kPasses; ++u) {
     const int g = tid + u * kI8Threads;
     if (g < G::kGroups) {
       uint32_t w[4];
@@ -190,6 +208,10 @@ __device__ __forceinline__ void splitSlot(const int8_t* win, int8_t* planes, int
 #pragma unroll
         for (int q = 0; q < 4; ++q) w[q] = __builtin_amdgcn_alignbyte(e[q + 1], e[q], 2);
       }
+      if ((w[0] | w[1] | w[2] | w[3]) == 0u) {
+        zf[u * kI8Waves + (tid >> 6)] = 1;
+        if ((tid & (kWave - 1)) < 4 * S - 4) zf[kZfStretches + u * kI8Waves + (tid >> 6)] = 1;
+      }
       uint4 iu, qu;
       int8IqToF16Units(w, iu, qu);
       const int unit = planeUnit(g >> 2, g & 3);
@@ -197,6 +219,24 @@ __device__ __forceinline__ void splitSlot(const int8_t* win, int8_t* planes, int
       *reinterpret_cast<uint4*>(planes + G::kPlaneBytes + 16 * unit) = qu;
     }
   }
+}
+
+// A flagged tile whose whole window (the planes' blocks 16 tile .. 16 tile + 14 + S) is zero: wave-uniform.
+// Its MFMA result is exactly 0 - no direct form needed (a long silence would otherwise pay for every tile).
+template <int S>
+__device__ __forceinline__ bool tileWindowZero(const int8_t* planes, int tile, int lane) {
+  constexpr int kUnits = 4 * (15 + S);  // per plane; the swizzle permutes units inside a block only
+  uint32_t any = 0u;
+#pragma unroll
+  for (int q = 0; q < (kUnits + kWave - 1) / kWave; ++q) {
+    const int unit = lane + kWave * q;
+    if (unit < kUnits) {
+      const uint4 a = *reinterpret_cast<const uint4*>(planes + 16 * (64 * tile + unit));
+      const uint4 b = *reinterpret_cast<const uint4*>(planes + I8Geom<S>::kPlaneBytes + 16 * (64 * tile + unit));
+      any |= a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w;
+    }
+  }
+  return __ballot((any & 0x7fff7fffu) != 0u) == 0ull;
 }
 
 // Tile MFMAs: 16 rows x 32 columns (512 outputs, I and Q) = S K-blocks x 2 K-halves x 2 limbs,
@@ -217,6 +257,37 @@ __device__ __forceinline__ void tileMfma(const int8_t* planes, const h8 (&bf)[S]
       const h8 av = *reinterpret_cast<const h8*>(plane + 16 * planeUnit(b0 + s, 2 * u + half));
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bf[s][u][0], acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bf[s][u][1], acc, 0, 0, 0);
+    }
+  }
+}
+
+// The guard's tile in the direct form, in the accumulator layout and units of tileMfma (x 2^sc; the
+// epilogue applies unchanged): the samples x' from the f16 planes (exact), the taps in fp32 from LDS - no
+// vector-memory operation, so the counted vmcnt waits of the DMA ring hold - accumulated in double (a
+// sequential fp32 sum of 127 products can reach 1e-6 of sum|h||x|). Rare tiles: one output at a time.
+template <int S>
+__device__ __forceinline__ void tileDirect(const int8_t* planes, const float* tapF, int T, int sc, int tile, int lane,
+                                           v16f& acc) {
+  constexpr int kPlaneBytes = I8Geom<S>::kPlaneBytes;
+  const int k0 = tile * kI8TileOut + 4 * (lane >> 5) * 32 + (lane & 31);  // tileEpilogue's rowOut
+  acc = v16f{};
+#pragma unroll 1
+  for (int i = 0; i < 8; ++i) {
+    const int k = k0 + 32 * ((i & 3) + 8 * (i >> 2));
+    double si = 0.0, sq = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < T; ++j) {
+      const int s = k + j;  // window sample: block s / 32, unit (s / 8) % 4, element s % 8
+      const int8_t* p = planes + 16 * planeUnit(s >> 5, (s >> 3) & 3) + 2 * (s & 7);
+      const double h = tapF[j];
+      si = fma(h, (double)*reinterpret_cast<const _Float16*>(p), si);
+      sq = fma(h, (double)*reinterpret_cast<const _Float16*>(p + kPlaneBytes), sq);
+    }
+    const float yi = (float)ldexp(si, sc), yq = (float)ldexp(sq, sc);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {  // register i without dynamic indexing
+      acc[r] = r == i ? yi : acc[r];
+      acc[r + 8] = r == i ? yq : acc[r + 8];
     }
   }
 }
@@ -244,9 +315,11 @@ __device__ __forceinline__ void tileEpilogue(const I8FirArgs& a, const v16f& acc
 
 template <int S, int EPI>
 __device__ __forceinline__ void computeTile(const I8FirArgs& a, const int8_t* planes, const h8 (&bf)[S][2][2],
-                                            int64_t chunkOut, int tile, int lane, float outScale) {
+                                            int64_t chunkOut, int tile, int lane, float outScale, bool direct,
+                                            const float* tapF, int sc) {
   v16f acc;
-  tileMfma<S>(planes, bf, tile, lane, acc);
+  if (direct && !tileWindowZero<S>(planes, tile, lane)) tileDirect<S>(planes, tapF, a.T, sc, tile, lane, acc);
+  else tileMfma<S>(planes, bf, tile, lane, acc);  // (wave-uniform)
   const int64_t tileOut = chunkOut + (int64_t)tile * kI8TileOut;
   if (tileOut + kI8TileOut <= a.nOut) tileEpilogue<EPI, true>(a, acc, tileOut, lane, outScale);
   else tileEpilogue<EPI, false>(a, acc, tileOut, lane, outScale);
@@ -259,6 +332,8 @@ __global__ __launch_bounds__(kI8Threads, GSDR_I8_BLOCKS_PER_CU) void firI8MfmaKe
   __shared__ __attribute__((aligned(16))) int8_t planes[2 * G::kPlaneBytes];
   __shared__ __attribute__((aligned(16))) _Float16 limbTab[2 * kLimbRow];
   __shared__ float waveMax[kI8Waves];
+  __shared__ float tapF[kTapWords];
+  __shared__ int zf[2][kZfWords];  // by chunk parity: chunk i + 1's are zeroed while chunk i's are read
 
   const int tid = threadIdx.x;
   const int lane = tid & (kWave - 1);
@@ -301,6 +376,8 @@ __global__ __launch_bounds__(kI8Threads, GSDR_I8_BLOCKS_PER_CU) void firI8MfmaKe
   vmWaitDyn<0, (kRing - 1) * kMaxPerChunk>(waveUniform(min(kRing - 1, n) * perChunk));
   asm volatile("" : "+v"(hv));  // hv is defined only after the wait
   hv = tid < T ? hv : 0.0f;
+  if (tid < kTapWords) tapF[tid] = hv;
+  if (tid < 2 * kZfWords) (&zf[0][0])[tid] = 0;
 
   // ---- taps -> block-uniform power-of-two scale, two f16 limbs --------------------------------
   float m = fabsf(hv);
@@ -355,7 +432,7 @@ __global__ __launch_bounds__(kI8Threads, GSDR_I8_BLOCKS_PER_CU) void firI8MfmaKe
     else vmWaitDyn<0, kSteady>(waveUniform(later));
     ldsBarrier();  // every wave's pieces of slot i landed; compute(i-1) done with the planes
     const int slot = i % kRing;
-    splitSlot<S>(ring + kRingPad + slot * G::kSlot + sub, planes, sub, tid);
+    splitSlot<S>(ring + kRingPad + slot * G::kSlot + sub, planes, zf[i & 1], sub, tid);
     if (a.carryDst != nullptr && T0 == 0 && i == 0) {
       // streaming history: the only block that reads samples [0, T - 1) has them in LDS now,
       // so the carry may overwrite them in place (source [nOut, nIn) is disjoint: nOut >= T - 1)
@@ -367,13 +444,20 @@ __global__ __launch_bounds__(kI8Threads, GSDR_I8_BLOCKS_PER_CU) void firI8MfmaKe
       issueChunk<S>(alignedBase, lastBlock, T0 + (i + kRing - 1) * kI8ChunkTiles,
                     ringLds + ((i + kRing - 1) % kRing) * G::kSlot, wave, lane);
     ldsBarrier();  // planes complete
+    if (tid < kZfWords) zf[(i + 1) & 1][tid] = 0;  // last read before the barrier at the top of this iteration
     const int c0 = T0 + i * kI8ChunkTiles;
     const int ct = min(kI8ChunkTiles, T0 + nt - c0);  // tiles in this chunk (< 8 only for the last)
     const int64_t chunkOut = (int64_t)c0 * kI8TileOut;
+    // the guard: tile t's window is stretch t and the head of stretch t + 1
+    int zt[kI8TilesPerWave];
+#pragma unroll
+    for (int t = 0; t < kI8TilesPerWave; ++t)
+      zt[t] = zf[i & 1][wave + kI8Waves * t] | zf[i & 1][kZfStretches + wave + kI8Waves * t + 1];
 #pragma unroll
     for (int t = 0; t < kI8TilesPerWave; ++t) {
       const int tile = wave + kI8Waves * t;  // a partial chunk spreads over the waves
-      if (tile < ct) computeTile<S, EPI>(a, planes, bf, chunkOut, tile, lane, outScale);
+      if (tile < ct)
+        computeTile<S, EPI>(a, planes, bf, chunkOut, tile, lane, outScale, waveUniform(zt[t]) != 0, tapF, sc);
     }
   }
   vmWait<0>();  // no DMA may still target this block's LDS when it exits

@@ -37,6 +37,8 @@ GSDR_CONV_API hipError_t gsdrInt8ToNormFloat(const int8_t* input, float* output,
 
 /* float -> int8 with the inverse scale, saturating and rounding to nearest even:
  *     output[i] = (int8_t)clamp(rintf(input[i] * 127.0f), -128, 127)
+ * in float32; +-inf saturate, and NaN gives -128 (the clamp is fminf(127, fmaxf(-128, v)), and fmaxf
+ * returns its other argument for a NaN). tests/test_gpu_parity.py pins all of it bit-exactly.
  * (format conversion for the egress side; not in the reference path). */
 GSDR_CONV_API hipError_t gsdrFloatToInt8(const float* input, int8_t* output, size_t numElements, int32_t device,
                                          hipStream_t stream);

@@ -187,6 +187,40 @@ def test_int8_to_float_all_codes_bit_exact(ops, orc, golden_dir):
         assert out.tobytes() == orc.int8_to_float(codes[off:]).tobytes()
 
 
+def _float_to_int8_ref(x):
+    """gsdrFloatToInt8's own expression in float32 (include/gsdr/conversion.h); NaN -> -128."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.clip(np.rint(x * np.float32(127.0)), np.float32(-128.0), np.float32(127.0))
+    return np.where(np.isnan(x), np.float32(-128.0), v).astype(np.int8)
+
+
+def test_float_to_int8_bit_exact(ops):
+    """gsdrFloatToInt8 against clip(rint(float32(x) * float32(127)), -128, 127): every code's k / 127, the
+    values either side of +-1, +-inf, +-0, denormals, 1e30, NaN (-> -128, as conversion.h states), a long random
+    vector, and input offsets of 1 and 3 elements."""
+    k = np.arange(-128, 128)
+    codes = (k / 127.0).astype(np.float32)
+    out = _host(ops.float_to_int8(_dev(codes)))
+    assert out.dtype == np.int8 and out.tolist() == k.tolist()
+    one = np.float32(1.0)
+    edge = np.array([np.nextafter(one, np.float32(0)), one, np.nextafter(one, np.float32(2)),
+                     -np.nextafter(one, np.float32(0)), -one, -np.nextafter(one, np.float32(2)),
+                     128.0 / 127.0, -128.0 / 127.0, -128.5 / 127.0, 127.5 / 127.0, 0.5 / 127.0, 1.5 / 127.0, 2.5 / 127.0,
+                     -0.5 / 127.0, np.inf, -np.inf, 0.0, -0.0, 1e-45, -1e-45, 1e-39, -1e-39, 1.17549435e-38, 1e30,
+                     -1e30, 3.4e38, -3.4e38], np.float32)
+    want = _float_to_int8_ref(edge)
+    assert want[[1, 4, 14, 15, 16, 17, 23, 24]].tolist() == [127, -127, 127, -128, 0, 0, 127, -128]
+    assert _host(ops.float_to_int8(_dev(edge))).tolist() == want.tolist()
+    nan = np.array([np.nan, -np.nan, 0.25, np.float32(np.nan)], np.float32)
+    assert _host(ops.float_to_int8(_dev(nan))).tolist() == [-128, -128, 32, -128]
+    rng = np.random.default_rng(8)
+    x = (rng.standard_normal(100_003) * 0.6).astype(np.float32)
+    x_d = _dev(x)
+    for off in (0, 1, 3):
+        assert _host(ops.float_to_int8(x_d[off:])).tobytes() == _float_to_int8_ref(x[off:]).tobytes(), off
+
+
 def test_am_demod_bit_exact(ops, orc, golden_dir):
     g = np.load(os.path.join(golden_dir, "am_golden.npz"))
     z = g["z"]
